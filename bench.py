@@ -20,7 +20,18 @@ Workloads:
        (the fp32 ring chain, cvae_f32chain.h, and its dW decode, cvae_f32wgrad.h).
   wide (BASELINE configs[4] shape): S=200, Z=512, 8+8 layers, bf16 (or --dtype fp8).
 
-Prints ONE JSON line (rank 0).  `roofline` is the dominant kernel's algorithmic
+Prints ONE JSON line (rank 0).  A plain run does what the headline figure needs and no more: set-up,
+the W warm-up steps, the K timed steps, the outputs when --dump-outputs is given, and the line
+(metric, value, unit, ms_per_step, dtype, config ...).  Everything below about `roofline` and
+`cpu_baseline` is measured in passes of its own and only with --full.
+
+--dump-outputs DIR writes what the last timed step left for its caller, copied off the device right
+after the timed steps and before anything else runs: `loss.npy` (the step's five loss terms: total,
+recon, kld, start, time) and `params.npy` (the flat fp32 master parameters after the step's Adam
+update), float32.  Model, data and eps are seeded, so two builds run with the same arguments can be
+compared array for array.
+
+--full: `roofline` is the dominant kernel's algorithmic
 FLOP per launch ÷ its average launch duration (the GEMM / MFMA roofline is the headline,
 BASELINE.json north_star; the HBM ceiling rides along in `other_ceiling`);
 `cpu_baseline` times the repo's CPU oracle (a torch-CPU restatement of the
@@ -29,10 +40,10 @@ container's CPU quota): the median of >= 200 steps after 20 warm-up steps (BASEL
 
 Timing: W warm-up steps, then the K timed steps without events (value, ms_per_step), issued
 through one prepared C call on one GPU (no per-call Python before the first launch) or replayed
-from a captured hipGraph on the data-parallel path; a second pass of the same K steps records
+from a captured hipGraph on the data-parallel path; with --full a second pass of the same K steps records
 each launch's own start/end timestamps for the per-kernel durations (roofline), since events
-inside the timed pass perturb it.  No step runs outside the W + K the JSON reports (graph
-captures execute nothing).
+inside the timed pass perturb it.  Without --full no step runs outside the W + K the JSON reports
+(graph captures execute nothing).
 """
 import argparse
 import json
@@ -210,6 +221,29 @@ def cpu_baseline(B, S, D, Z, H, seconds, n_enc=4, n_dec=4, data=None, min_steps=
                       f"{sum(times) / len(times) * 1e3:.3f} mean, {threads} threads"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as ``directory/<name>.npy`` (float32; float64 stays float64).  When the
+    arrays together exceed ``limit`` bytes, every array over its equal share is cut to a fixed
+    sample of its flattened elements (sorted indices from a generator seeded with 0, the same in
+    every run and build).  Returns {name: elements written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[k] = a.reshape(-1)[keep]
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return {k: int(a.size) for k, a in arrays.items()}
+
+
 def launch_plan(gpus, env, device_count):
     """What ``bench.py --gpus N`` does with the process it runs in (decided before any GPU call:
     ``torch.cuda.device_count()`` does not initialise the GPU on this image).
@@ -366,13 +400,21 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="split step issued eagerly (no hipGraph)")
     ap.add_argument("--graph-steps", type=int, default=8,
                     help="training steps captured per graph replay (a remainder runs a 1-step graph)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss.npy, params.npy; float32) "
+                         "into DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each in a pass of its own: "
+                         "per-kernel durations and the roofline (the K steps again with events), the "
+                         "back-to-back single-kernel pass, the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
-                    help="CPU baseline: time at least this long (and at least 200 steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full, CPU baseline: time at least this long (and at least 200 steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-b2b", action="store_true",
-                    help="skip the back-to-back single-kernel pass (profiling runs: rocprof then sees step launches only)")
+                    help="--full without the back-to-back single-kernel pass (profiling runs: rocprof then sees "
+                         "step launches only)")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic.json"),
-                    help="per-launch HBM traffic from rocprofv3 --pmc passes (scripts/pmc_traffic.py)")
+                    help="--full: per-launch HBM traffic from rocprofv3 --pmc passes (scripts/pmc_traffic.py)")
     args = ap.parse_args()
     what, arg = launch_plan(args.gpus, os.environ, torch.cuda.device_count())
     if what == "error":
@@ -546,6 +588,11 @@ def main():
     if world > 1:
         dist.barrier()
     t = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, copied before any other launch touches them
+        dumped = dump_outputs(args.dump_outputs, {"loss": eng.loss.detach().float().cpu().numpy(),
+                                                  "params": eng.params.detach().float().cpu().numpy()})
     verified_after = None
     if dp.px is not None:
         # the exchange checked again over the state the timed steps left (collective; every rank's
@@ -569,20 +616,21 @@ def main():
     # kernel durations for the roofline: the same K steps again with HIP events recorded on the
     # launch stream between kernels (events inside the timed pass would add ~10 us per step;
     # graph replays record none, so this pass runs eagerly)
-    eng.set_timing(True)
-    if wl != "cfg1" and graphed is not None:
-        for _ in range(args.steps):
-            dp.step(x, batch=B, global_batch=B * world, **ckw)
-    else:
-        run(args.steps)
-    torch.cuda.synchronize(dev)
-    kt = eng.kernel_times()
-    eng.set_timing(False)
-    # each kernel alone, launched back-to-back (cvae_bench_kernels): the step's kernels without
-    # their neighbours' cache/instruction-cache effects
-    b2b = None
-    if not args.no_b2b and wl not in ("cfg1", "cfg4") and world == 1:
-        b2b = eng.bench_kernels(x, max(args.steps, 20), batch=B)
+    kt = b2b = None
+    if args.full:
+        eng.set_timing(True)
+        if wl != "cfg1" and graphed is not None:
+            for _ in range(args.steps):
+                dp.step(x, batch=B, global_batch=B * world, **ckw)
+        else:
+            run(args.steps)
+        torch.cuda.synchronize(dev)
+        kt = eng.kernel_times()
+        eng.set_timing(False)
+        # each kernel alone, launched back-to-back (cvae_bench_kernels): the step's kernels without
+        # their neighbours' cache/instruction-cache effects
+        if not args.no_b2b and wl not in ("cfg1", "cfg4") and world == 1:
+            b2b = eng.bench_kernels(x, max(args.steps, 20), batch=B)
     if world > 1:
         tt = torch.tensor([t], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -593,39 +641,41 @@ def main():
     px_stats = dp.px.stats() if dp.px is not None else None
     if rank == 0:
         fl = flops_per_traj(S, D, Z, H, n_enc=NE, n_dec=ND, E=CE)
-        tsize = 4 if dtype == "fp32" else 2  # fp8: bf16 activations
-        bt = bytes_per_traj(S, D, Z, H, tsize, n_enc=NE, n_dec=ND)
-        n_par = eng.n_params
-        rows_launch = rows_per_step if wl == "cfg1" else B
-        flop = {k: fl["rowchain" if k.startswith("rowchain") else "wgrad"] * rows_launch
-                for k in ("rowchain", "wgrad", "wgrad_adam", "wgrad_dec", "wgrad_rest")}
-        nbytes = {"rowchain": bt["rowchain"] * rows_launch, "wgrad": bt["wgrad"] * rows_launch + 4 * n_par,
-                  "wgrad_adam": bt["wgrad"] * rows_launch + ADAM_BYTES_PER_PARAM * n_par,
-                  "wgrad_dec": bt["wgrad"] * rows_launch, "wgrad_rest": bt["wgrad"] * rows_launch}
-        flop["fused_step"] = flop["rowchain"] + flop["wgrad_adam"]
-        nbytes["fused_step"] = nbytes["rowchain"] + nbytes["wgrad_adam"]
-        flop["adam"], nbytes["adam"] = 0, ADAM_BYTES_PER_PARAM * n_par
-        # peer exchange: every dW tile over the local rows + Adam on this rank's 1/world of the tiles
-        flop["px_wgrad"] = flop["wgrad"]
-        nbytes["px_wgrad"] = bt["wgrad"] * rows_launch + ADAM_BYTES_PER_PARAM * n_par // max(world, 1)
-        dom = max((k for k in kt if k in flop and flop[k] > 0), key=lambda k: kt[k][0])
-        std = (S, D, Z, H, NE, ND) == (100, 6, 8, 128, 4, 4)
-        # BASELINE cfg5's shape: its own committed pass (gpu_round.sh, profiles/traffic_wide_<dtype>.json)
-        tfile = args.traffic_file if std else (os.path.join(ROOT, "profiles", f"traffic_wide_{dtype}.json")
-                                              if (S, D, Z, H, NE, ND) == (200, 6, 512, 128, 8, 8) else None)
-        traffic = measured_traffic(tfile, dom, B, dtype) if tfile else None
-        roof = roofline(dom, kt[dom][0], flop[dom], nbytes[dom], dtype, traffic)
-        if "rowchain" in kt and wl != "cfg1":
-            wsb = weight_stream_bytes(S, D, Z, H, dtype, n_enc=NE, n_dec=ND)
-            ach = wsb / (kt["rowchain"][0] * 1e-3) / 1e9
-            roof["weight_stream"] = {"kernel": "rowchain", "bytes_per_workgroup": wsb,
-                                     "achieved_GBps_per_CU": round(ach, 1),
-                                     "measured_max_GBps_per_CU": CU_STREAM_MAX_GBS,
-                                     "frac": round(ach / CU_STREAM_MAX_GBS, 4),
-                                     "active_CUs": (rows_launch + 15) // 16}
-        roof["kernels_ms"] = {k: round(v[0], 5) for k, v in kt.items()}
-        if b2b:
-            roof["kernels_back_to_back_ms"] = {k: round(v, 5) for k, v in b2b.items()}
+        roof = None
+        if kt is not None:  # --full: the timing pass ran
+            tsize = 4 if dtype == "fp32" else 2  # fp8: bf16 activations
+            bt = bytes_per_traj(S, D, Z, H, tsize, n_enc=NE, n_dec=ND)
+            n_par = eng.n_params
+            rows_launch = rows_per_step if wl == "cfg1" else B
+            flop = {k: fl["rowchain" if k.startswith("rowchain") else "wgrad"] * rows_launch
+                    for k in ("rowchain", "wgrad", "wgrad_adam", "wgrad_dec", "wgrad_rest")}
+            nbytes = {"rowchain": bt["rowchain"] * rows_launch, "wgrad": bt["wgrad"] * rows_launch + 4 * n_par,
+                      "wgrad_adam": bt["wgrad"] * rows_launch + ADAM_BYTES_PER_PARAM * n_par,
+                      "wgrad_dec": bt["wgrad"] * rows_launch, "wgrad_rest": bt["wgrad"] * rows_launch}
+            flop["fused_step"] = flop["rowchain"] + flop["wgrad_adam"]
+            nbytes["fused_step"] = nbytes["rowchain"] + nbytes["wgrad_adam"]
+            flop["adam"], nbytes["adam"] = 0, ADAM_BYTES_PER_PARAM * n_par
+            # peer exchange: every dW tile over the local rows + Adam on this rank's 1/world of the tiles
+            flop["px_wgrad"] = flop["wgrad"]
+            nbytes["px_wgrad"] = bt["wgrad"] * rows_launch + ADAM_BYTES_PER_PARAM * n_par // max(world, 1)
+            dom = max((k for k in kt if k in flop and flop[k] > 0), key=lambda k: kt[k][0])
+            std = (S, D, Z, H, NE, ND) == (100, 6, 8, 128, 4, 4)
+            # BASELINE cfg5's shape: its own committed pass (gpu_round.sh, profiles/traffic_wide_<dtype>.json)
+            tfile = args.traffic_file if std else (os.path.join(ROOT, "profiles", f"traffic_wide_{dtype}.json")
+                                                  if (S, D, Z, H, NE, ND) == (200, 6, 512, 128, 8, 8) else None)
+            traffic = measured_traffic(tfile, dom, B, dtype) if tfile else None
+            roof = roofline(dom, kt[dom][0], flop[dom], nbytes[dom], dtype, traffic)
+            if "rowchain" in kt and wl != "cfg1":
+                wsb = weight_stream_bytes(S, D, Z, H, dtype, n_enc=NE, n_dec=ND)
+                ach = wsb / (kt["rowchain"][0] * 1e-3) / 1e9
+                roof["weight_stream"] = {"kernel": "rowchain", "bytes_per_workgroup": wsb,
+                                         "achieved_GBps_per_CU": round(ach, 1),
+                                         "measured_max_GBps_per_CU": CU_STREAM_MAX_GBS,
+                                         "frac": round(ach / CU_STREAM_MAX_GBS, 4),
+                                         "active_CUs": (rows_launch + 15) // 16}
+            roof["kernels_ms"] = {k: round(v[0], 5) for k, v in kt.items()}
+            if b2b:
+                roof["kernels_back_to_back_ms"] = {k: round(v, 5) for k, v in b2b.items()}
         value = world * rows_per_step * args.steps / t
         if wl == "cfg2":
             metric = "trajectories/sec per ELBO step, batch=1024 seq_len=100; 1/2/4/8 MI355X"
@@ -661,8 +711,11 @@ def main():
                           "global_batch": B * world, "seq_len": S, "state_dim": D, "latent_dim": Z,
                           "hidden_dim": H, "parallelism": f"dp{world}" + (" (rehearsal: all ranks on GPU 0)"
                                                                           if share else "")},
-               "roofline": roof,
                "flop_per_traj": fl["total"]}
+        if roof is not None:
+            res["roofline"] = roof
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
         if px_stats is not None:
             res["exchange_waits_rank0"] = px_stats
             k_gpu, g_blocks = dp.px.layout()
@@ -672,7 +725,7 @@ def main():
             res["exchange_verified"] = verified
         if verified_after is not None:  # the same check after the timed steps (a failure exits above)
             res["exchange_verified_after"] = verified_after
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(B, S, D, Z, H, args.cpu_seconds, NE, ND,
                                                data=data_cpu if wl == "cfg1" else None)
             res["speedup_vs_cpu"] = round(value / res["cpu_baseline"]["value"], 1)

@@ -3,7 +3,7 @@
 # are garbage; only the kernel times matter), fastchain (default) and the ring chain.
 set -u
 O=gpurun_out/floors; mkdir -p $O
-B="timeout -k 10 120 python -u bench.py --no-cpu-baseline --steps 200"
+B="timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --steps 200"
 for v in nowl nost both; do
   for ring in 0 1; do
     CVAE_RING=$ring CVAE_LIB=$PWD/build/diag/$v.so $B > $O/bench_${v}_r$ring.json 2> $O/bench_${v}_r$ring.err || { tail -5 $O/bench_${v}_r$ring.err; exit 1; }

@@ -6,7 +6,7 @@ set -u
 O=gpurun_out/fring2; mkdir -p $O
 timeout -k 10 300 python3 -u -m pytest tests/test_hip_parity.py -m gpu -x -q -k fused_ring --timeout 120 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-B="timeout -k 10 120 python3 bench.py --no-cpu-baseline --steps 200 --warmup 20"
+B="timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --steps 200 --warmup 20"
 for i in 1 2; do
   for m in 0 1 2 3; do CVAE_FUSE_RING=$m $B > $O/m${m}_$i.json 2> $O/m${m}_$i.err || { tail -5 $O/m${m}_$i.err; exit 1; }; done
 done

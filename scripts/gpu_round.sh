@@ -15,9 +15,9 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 fi
 for r in a b; do
-  timeout -k 10 180 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_s20_$r.json 2> $OUT/bench_s20_$r.err || exit 1
+  timeout -k 10 180 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_s20_$r.json 2> $OUT/bench_s20_$r.err || exit 1
 done
-B="timeout -k 10 180 python3 bench.py --no-cpu-baseline"
+B="timeout -k 10 180 python3 bench.py --full --no-cpu-baseline"
 $B --steps 200 --warmup 20 > $OUT/bench_s200.json 2> $OUT/bench_s200.err &&
 $B --steps 200 --warmup 20 --dp > $OUT/bench_dp.json 2> $OUT/bench_dp.err &&
 $B --steps 200 --warmup 20 --dp --buckets 2 > $OUT/bench_dp_b2.json 2> $OUT/bench_dp_b2.err &&
@@ -25,15 +25,15 @@ $B --steps 200 --warmup 20 --workload cfg4 > $OUT/bench_cfg4.json 2> $OUT/bench_
 $B --steps 100 --warmup 10 --workload wide > $OUT/bench_wide_bf16.json 2> $OUT/bench_wide_bf16.err &&
 $B --steps 100 --warmup 10 --workload wide --dtype fp8 > $OUT/bench_wide_fp8.json 2> $OUT/bench_wide_fp8.err &&
 CVAE_FP8_DW=mx $B --steps 100 --warmup 10 --workload wide --dtype fp8 > $OUT/bench_wide_fp8_mxdw.json 2> $OUT/bench_wide_fp8_mxdw.err &&
-timeout -k 10 180 python3 bench.py --workload cfg1 --steps 50 --warmup 5 > $OUT/bench_cfg1.json 2> $OUT/bench_cfg1.err || { tail -5 $OUT/*.err; exit 1; }
+timeout -k 10 180 python3 bench.py --full --workload cfg1 --steps 50 --warmup 5 > $OUT/bench_cfg1.json 2> $OUT/bench_cfg1.err || { tail -5 $OUT/*.err; exit 1; }
 # the N > 1 path rehearsed on the one GPU: bench.py starting its own N ranks (the plain --gpus N form),
 # and once under torch.distributed.run (the driver's form)
 for n in 2 4 8; do
-  CVAE_BENCH_SHARE_GPU=1 CVAE_PX_TIMEOUT_MS=30000 timeout -k 10 400 python3 bench.py --gpus $n --steps 20 --warmup 5 \
+  CVAE_BENCH_SHARE_GPU=1 CVAE_PX_TIMEOUT_MS=30000 timeout -k 10 400 python3 bench.py --full --gpus $n --steps 20 --warmup 5 \
     > $OUT/bench_share$n.json 2> $OUT/bench_share$n.err || { tail -5 $OUT/bench_share$n.err; exit 1; }
 done
 CVAE_BENCH_SHARE_GPU=1 CVAE_PX_TIMEOUT_MS=30000 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29582 bench.py --gpus 2 --steps 20 --warmup 5 \
+  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29582 bench.py --full --gpus 2 --steps 20 --warmup 5 \
   > $OUT/bench_share2_torchrun.json 2> $OUT/bench_share2_torchrun.err || { tail -5 $OUT/bench_share2_torchrun.err; exit 1; }
 for f in $OUT/bench_*.json; do python3 -c "import json;d=json.load(open('$f'));r=d['roofline'];print('$f',d['value'],d['ms_per_step'],r.get('kernels_ms'),r['frac'])"; done
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0

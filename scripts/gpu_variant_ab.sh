@@ -7,7 +7,7 @@ set -u
 O=${O:-gpurun_out/vab}; mkdir -p $O
 DIR=${DIR:-build/diag}
 EX="${EXTRA:-}"; [ "${WIDE:-0}" = 1 ] && EX="--workload wide --dtype ${DT:-bf16} --steps 100 --warmup 10"
-B="timeout -k 10 120 python -u bench.py --no-cpu-baseline --steps 400 $EX"
+B="timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --steps 400 $EX"
 for i in $(seq 1 ${REPS:-2}); do
   $B > $O/base$i.json 2> $O/base$i.err || exit 1
   for v in ${VARIANTS:-}; do CVAE_LIB=$PWD/$DIR/$v.so $B > $O/${v}_$i.json 2> $O/${v}_$i.err || { tail -3 $O/${v}_$i.err; exit 1; }; done

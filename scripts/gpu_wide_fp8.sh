@@ -7,7 +7,7 @@ O=${O:-gpurun_out/wide_fp8}; mkdir -p $O
 timeout -k 10 600 python3 -u -m pytest tests/test_hip_parity.py -m gpu -x -v -rP -k "fp8 or wide" \
   --timeout 280 --timeout-method thread > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 grep -E "PASSED|FAILED" $O/tests.log | tail -20
-B="timeout -k 10 180 python3 bench.py --no-cpu-baseline --steps 100 --warmup 10 --workload wide"
+B="timeout -k 10 180 python3 bench.py --full --no-cpu-baseline --steps 100 --warmup 10 --workload wide"
 for i in 1 2; do
   $B > $O/wide_bf16_$i.json 2> $O/wide_bf16_$i.err && $B --dtype fp8 > $O/wide_fp8_$i.json 2> $O/wide_fp8_$i.err \
     || { tail -5 $O/*.err; exit 1; }

@@ -9,6 +9,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH="$GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-b2b --steps $STEPS --warmup 5 ${BENCH_EXTRA:-}"  # BENCH_EXTRA: e.g. --workload wide --dtype fp8
+BENCH="$BENCH --full"  # with the per-kernel timing pass (the K steps a second time, events between kernels)
 P=${PASSES:-trace,sq1,sq2,sq3,ta,tcc,fetch,write}
 has() { case ",$P," in *",$1,"*) return 0;; *) return 1;; esac; }
 if has trace; then

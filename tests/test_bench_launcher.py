@@ -127,3 +127,39 @@ def test_run_ranks_bounds_a_peer_left_behind_by_a_clean_exit():
                          done_grace_s=1)
     assert time.monotonic() - t0 < 30
     assert rc != 0
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one .npy per array, float32 (float64 kept), values unchanged."""
+    import numpy as np
+    a = np.arange(12, dtype=np.float32).reshape(3, 4)
+    n = bench.dump_outputs(str(tmp_path / "d"), {"a": a, "b": a.astype(np.float64) / 3, "h": a.astype(np.float16)})
+    assert n == {"a": 12, "b": 12, "h": 12}
+    assert sorted(os.listdir(tmp_path / "d")) == ["a.npy", "b.npy", "h.npy"]
+    got = {k: np.load(tmp_path / "d" / (k + ".npy")) for k in n}
+    assert got["a"].dtype == np.float32 and got["b"].dtype == np.float64 and got["h"].dtype == np.float32
+    np.testing.assert_array_equal(got["a"], a)
+    np.testing.assert_array_equal(got["b"], a.astype(np.float64) / 3)
+    np.testing.assert_array_equal(got["h"], a)
+
+
+def test_dump_outputs_samples_over_the_limit(tmp_path):
+    """Over the byte limit an array is cut to a fixed sample of its elements: within the limit in all,
+    the same elements in every run, each one a value of the array at a known index."""
+    import numpy as np
+    big = np.arange(1000, dtype=np.float32)
+    small = np.arange(10, dtype=np.float32)
+    for d in ("x", "y"):
+        n = bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, limit=800)
+    assert n == {"big": 100, "small": 10}
+    gx, gy = np.load(tmp_path / "x" / "big.npy"), np.load(tmp_path / "y" / "big.npy")
+    assert gx.nbytes + small.nbytes <= 800
+    np.testing.assert_array_equal(gx, gy)
+    assert len(set(gx.tolist())) == 100 and (np.diff(gx) > 0).all()  # distinct indices, in order
+    np.testing.assert_array_equal(np.load(tmp_path / "x" / "small.npy"), small)
+
+
+def test_cli_has_full_and_dump_outputs():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
