@@ -26,6 +26,7 @@
 #include "cvae_f32wgrad.h"
 #include "cvae_extract.h"
 #include "cvae_mpc.h"
+#include "cvae_metrics.h"
 
 namespace {
 
@@ -2125,6 +2126,112 @@ int cvae_mpc_reference(int n_paths, const double* waypoints, const int32_t* wp_o
                             (int)lds));
   hipLaunchKernelGGL(mpc_reference_kernel, dim3(n_paths), dim3(64), lds, (hipStream_t)stream, waypoints, wp_offsets,
                      initial_states, t, n_t, out, scalars);
+  HIPCK(hipGetLastError());
+  return CVAE_OK;
+}
+
+static int val_cfg(const cvae_val_config* in, ValCfg* c, int* waves) {
+  if (!in) return fail(CVAE_E_INVALID, "null config");
+  if (in->stride < 2 || in->stride > 16) return fail(CVAE_E_INVALID, "stride must be in [2, 16]");
+  const int cols[] = {in->x_col, in->y_col, in->coord_col};
+  for (int k : cols)
+    if (k < 0 || k >= in->stride) return fail(CVAE_E_INVALID, "column index outside the row");
+  if (in->t_col >= in->stride || in->v_col >= in->stride) return fail(CVAE_E_INVALID, "column index outside the row");
+  if (in->t_col < 0 && !(in->dt > 0.0)) return fail(CVAE_E_INVALID, "dt must be > 0 when t is the row index");
+  if (in->subsample < 0 || in->surf_min_rows < 0 || in->block_waves < 0 || in->block_waves > VAL_MAX_WAVES)
+    return fail(CVAE_E_INVALID, "bad validation parameter");
+  const int ne[] = {in->n_v_edges, in->n_x_edges, in->n_y_edges, in->n_coord_edges, in->n_time_edges};
+  for (int n : ne)
+    if (n < 0 || n == 1 || n > VAL_MAX_EDGES) return fail(CVAE_E_INVALID, "at most 1024 edges per axis (and not 1)");
+  if (in->n_slice_edges < 0 || in->n_slice_edges > VAL_MAX_SLICES + 1)
+    return fail(CVAE_E_INVALID, "at most 4096 time slices");
+  if ((in->n_x_edges == 0) != (in->n_y_edges == 0) || (in->n_coord_edges == 0) != (in->n_time_edges == 0))
+    return fail(CVAE_E_INVALID, "grid and surface edges come in pairs");
+  if (in->n_x_edges && (int64_t)(in->n_x_edges - 1) * (in->n_y_edges - 1) > VAL_MAX_CELLS)
+    return fail(CVAE_E_INVALID, "at most 65536 cells per grid");
+  if (in->n_coord_edges && (int64_t)(in->n_coord_edges - 1) * (in->n_time_edges - 1) > VAL_MAX_SURF)
+    return fail(CVAE_E_INVALID, "at most 4096 surface cells");
+  c->dt = in->dt; c->stride = in->stride; c->x_col = in->x_col; c->y_col = in->y_col; c->t_col = in->t_col;
+  c->v_col = in->v_col; c->coord_col = in->coord_col; c->subsample = in->subsample;
+  c->surf_min_rows = in->surf_min_rows;
+  c->n_v = in->n_v_edges; c->n_x = in->n_x_edges; c->n_y = in->n_y_edges; c->n_c = in->n_coord_edges;
+  c->n_t = in->n_time_edges; c->n_s = in->n_slice_edges < 2 ? 0 : in->n_slice_edges;
+  *waves = in->block_waves ? in->block_waves : 4;
+  return CVAE_OK;
+}
+
+// offsets_host: the host's copy of the row-offset table, validated before anything is launched
+static int val_offsets(int n_traj, int64_t n_rows, const int64_t* offsets_host) {
+  if (n_traj < 0 || n_rows < 0) return fail(CVAE_E_INVALID, "bad size");
+  if (!offsets_host) return fail(CVAE_E_INVALID, "null argument");
+  if (offsets_host[0] < 0) return fail(CVAE_E_INVALID, "row offsets must start at >= 0");
+  for (int p = 0; p < n_traj; ++p)
+    if (offsets_host[p + 1] < offsets_host[p]) return fail(CVAE_E_INVALID, "row offsets must be monotone");
+  if (offsets_host[n_traj] != n_rows) return fail(CVAE_E_INVALID, "row offsets must end at n_rows");
+  if (n_rows >= ((int64_t)1 << 28)) return fail(CVAE_E_INVALID, "at most 2^28 - 1 points per call");
+  return CVAE_OK;
+}
+
+static int val_grid(int n_traj, int waves) { return std::max(1, std::min((n_traj + waves - 1) / waves, 1024)); }
+
+int cvae_val_ranges(const cvae_val_config* cfg, int n_traj, const double* rows, int64_t n_rows,
+                    const int64_t* offsets, const int64_t* offsets_host, const double* v, uint64_t* out,
+                    void* stream) {
+  ValCfg c;
+  int waves;
+  int rc = val_cfg(cfg, &c, &waves);
+  if (rc) return rc;
+  if ((rc = val_offsets(n_traj, n_rows, offsets_host))) return rc;
+  if (!out) return fail(CVAE_E_INVALID, "null argument");
+  hipLaunchKernelGGL(val_ranges_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)out);
+  HIPCK(hipGetLastError());
+  if (n_traj == 0 || n_rows == 0) return CVAE_OK;  // nothing that reads is launched
+  if (!rows || !offsets || (c.v_col < 0 && !v)) return fail(CVAE_E_INVALID, "null argument");
+  hipLaunchKernelGGL(val_ranges_kernel, dim3(val_grid(n_traj, waves)), dim3(64 * waves), 0, (hipStream_t)stream, c,
+                     n_traj, rows, offsets, n_rows, v, (unsigned long long*)out);
+  HIPCK(hipGetLastError());
+  return CVAE_OK;
+}
+
+static double val_unkey(uint64_t k) {
+  const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double d;
+  memcpy(&d, &b, 8);
+  return d;
+}
+
+int cvae_val_accumulate(const cvae_val_config* cfg, int n_traj, const double* rows, int64_t n_rows,
+                        const int64_t* offsets, const int64_t* offsets_host, const double* v_hist,
+                        const double* v_surf, const double* edges, const uint64_t* ranges_host,
+                        const cvae_val_tables* tables, void* stream) {
+  ValCfg c;
+  int waves;
+  int rc = val_cfg(cfg, &c, &waves);
+  if (rc) return rc;
+  if ((rc = val_offsets(n_traj, n_rows, offsets_host))) return rc;
+  if (!tables || !ranges_host) return fail(CVAE_E_INVALID, "null argument");
+  if ((c.n_v && !tables->hist_v) || (c.n_x && (!tables->h_points || !tables->h_traj)) ||
+      (c.n_c && (!tables->surf_cnt || !tables->surf_sum)) ||
+      (c.n_s && (!tables->slice_cnt || !tables->slice_sx || !tables->slice_sy)))
+    return fail(CVAE_E_INVALID, "null table");
+  if (n_traj == 0 || n_rows == 0) return CVAE_OK;
+  if (!rows || !offsets || !edges || (c.v_col < 0 && ((c.n_v && !v_hist) || (c.n_c && !v_surf))))
+    return fail(CVAE_E_INVALID, "null argument");
+  // the fixed-point sums hold |sum| < 2^62 for |value| < 1024 and < 2^28 points (checked above)
+  if (ranges_host[VAL_R_COUNT] != (uint64_t)n_rows) return fail(CVAE_E_INVALID, "ranges are of another population");
+  for (int k = 0; k < 6; ++k) {  // v, x, y min/max
+    const double d = val_unkey(ranges_host[k]);
+    if (!(std::fabs(d) < 1024.0)) return fail(CVAE_E_INVALID, "values must be finite and |value| < 1024");
+  }
+  ValTables T = {tables->hist_v, tables->h_points, tables->h_traj, tables->surf_cnt, (long long*)tables->surf_sum,
+                 tables->slice_cnt, (long long*)tables->slice_sx, (long long*)tables->slice_sy};
+  size_t lds = val_lds_bytes(c, waves);
+  while (lds > 150 * 1024 && waves > 1) lds = val_lds_bytes(c, --waves);
+  if (lds > 150 * 1024) return fail(CVAE_E_INVALID, "tables do not fit the LDS");
+  HIPCK(hipFuncSetAttribute((const void*)val_accumulate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds));
+  hipLaunchKernelGGL(val_accumulate_kernel, dim3(val_grid(n_traj, waves)), dim3(64 * waves), lds,
+                     (hipStream_t)stream, c, n_traj, rows, offsets, n_rows, v_hist, v_surf, edges, T);
   HIPCK(hipGetLastError());
   return CVAE_OK;
 }

@@ -30,6 +30,18 @@ class CvaeMpcConfig(C.Structure):
                [(k, C.c_int) for k in ("prediction_horizon", "control_horizon", "max_iter", "reserved")]
 
 
+class CvaeValConfig(C.Structure):
+    _fields_ = [("dt", C.c_double)] + \
+               [(k, C.c_int) for k in ("stride", "x_col", "y_col", "t_col", "v_col", "coord_col", "subsample",
+                                       "surf_min_rows", "n_v_edges", "n_x_edges", "n_y_edges", "n_coord_edges",
+                                       "n_time_edges", "n_slice_edges", "block_waves")]
+
+
+class CvaeValTables(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("hist_v", "h_points", "h_traj", "surf_cnt", "surf_sum", "slice_cnt",
+                                          "slice_sx", "slice_sy")]
+
+
 class CvaeAdamConfig(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
@@ -113,6 +125,11 @@ _SIGS = {
     "cvae_mpc_solve": (_i, [C.POINTER(CvaeMpcConfig), _i, _v, _v, _v, _v, _v, _v, _v]),
     # n_paths, waypoints, wp_offsets, initial_states, t, n_t, out, scalars, stream
     "cvae_mpc_reference": (_i, [_i, _v, _v, _v, _v, _i, _v, _v, _v]),
+    # cfg, n_traj, rows, n_rows, offsets, offsets_host, v, out, stream
+    "cvae_val_ranges": (_i, [C.POINTER(CvaeValConfig), _i, _v, _i64, _v, _v, _v, _v, _v]),
+    # cfg, n_traj, rows, n_rows, offsets, offsets_host, v_hist, v_surf, edges, ranges_host, tables, stream
+    "cvae_val_accumulate": (_i, [C.POINTER(CvaeValConfig), _i, _v, _i64, _v, _v, _v, _v, _v, _v,
+                                 C.POINTER(CvaeValTables), _v]),
     "cvae_set_timing": (_i, [_v, _i]),
     "cvae_kernel_times": (_i, [_v, C.c_char_p, _i, C.POINTER(_f), _i]),
     "cvae_last_error": (C.c_char_p, []),

@@ -83,13 +83,24 @@ def _pack(waypoints_list, initial_states, dev):
             torch.from_numpy(np.ascontiguousarray(init)).to(dev))
 
 
-def track_batch(waypoints_list, initial_states, total_times=None, device="cuda", return_iters=False, **cfg):
-    """``PathTracker(wp, init, ...).run_simulation(total_time)`` for every path at once.
+class DeviceTracks:
+    """Tracked states left on the device, in the ragged layout ``cvae_mpc_track`` writes: ``states``
+    float64 [tot + P, 4] (x, y, theta, v), path p owning rows [offsets[p], offsets[p+1]) (int64
+    [P+1]; ``offsets`` on the device, ``offsets_host`` the same table as a numpy array), ``dt`` the
+    tracker's time step.  ``controls`` / ``iters`` / ``n_steps`` / ``step_offsets`` as the launch
+    left them (``n_steps`` and ``step_offsets`` on the host)."""
 
-    waypoints_list: sequence of [n_p, 3] (x, y, t) arrays; initial_states: [P, 5] (x, y, theta,
-    vx, vy) — theta is wrapped here as the reference's constructor does (the caller's array is
-    not modified); total_times: per path (default: the path's last waypoint time, as
-    ``Distribution.py:104``).  Returns a list of (times, states, controls) per path."""
+    def __init__(self, states, offsets, offsets_host, dt, controls, iters, n_steps, step_offsets):
+        self.states, self.offsets, self.offsets_host, self.dt = states, offsets, offsets_host, dt
+        self.controls, self.iters, self.n_steps, self.step_offsets = controls, iters, n_steps, step_offsets
+
+    def __len__(self):
+        return len(self.offsets_host) - 1
+
+
+def track_batch_device(waypoints_list, initial_states, total_times=None, device="cuda", **cfg):
+    """``track_batch`` without the copy to the host and the split: the same arguments, the same
+    launch; returns a ``DeviceTracks`` (what ``validate.metrics`` consumes)."""
     torch = _torch()
     c = mpc_config(**cfg)
     dev = torch.device(device)
@@ -114,13 +125,26 @@ def track_batch(waypoints_list, initial_states, total_times=None, device="cuda",
     d_it = torch.empty(max(tot, 1), dtype=torch.int32, device=dev)
     check(lib().cvae_mpc_track(C.byref(c), P, _ptr(d_wp), _ptr(d_off), _ptr(d_init), _ptr(d_ns), _ptr(d_so),
                                _ptr(d_states), _ptr(d_ctrl), _ptr(d_it), _stream(torch, dev)), "cvae_mpc_track")
-    states, ctrl, its = d_states.cpu().numpy(), d_ctrl.cpu().numpy(), d_it.cpu().numpy()
+    roff = soff + np.arange(P + 1, dtype=np.int64)  # path p: rows [soff[p] + p, soff[p+1] + p + 1)
+    return DeviceTracks(d_states, torch.from_numpy(roff).to(dev), roff, float(c.dt), d_ctrl, d_it, n_steps, soff)
+
+
+def track_batch(waypoints_list, initial_states, total_times=None, device="cuda", return_iters=False, **cfg):
+    """``PathTracker(wp, init, ...).run_simulation(total_time)`` for every path at once.
+
+    waypoints_list: sequence of [n_p, 3] (x, y, t) arrays; initial_states: [P, 5] (x, y, theta,
+    vx, vy) — theta is wrapped here as the reference's constructor does (the caller's array is
+    not modified); total_times: per path (default: the path's last waypoint time, as
+    ``Distribution.py:104``).  Returns a list of (times, states, controls) per path."""
+    d = track_batch_device(waypoints_list, initial_states, total_times, device, **cfg)
+    P, n_steps, soff, dt = len(d), d.n_steps, d.step_offsets, d.dt
+    states, ctrl, its = d.states.cpu().numpy(), d.controls.cpu().numpy(), d.iters.cpu().numpy()
     out = []
     for p in range(P):
         ns, o = int(n_steps[p]), int(soff[p])
         times = np.empty(ns + 1)
         times[0] = 0.0
-        times[1:] = np.arange(ns) * c.dt + c.dt  # current_time + dt, current_time = i * dt (:491, :513)
+        times[1:] = np.arange(ns) * dt + dt  # current_time + dt, current_time = i * dt (:491, :513)
         r = (times, states[o + p:o + p + ns + 1].copy(), ctrl[o:o + ns].copy().reshape(ns, 2))
         out.append(r + (its[o:o + ns].copy(),) if return_iters else r)
     return out

@@ -497,6 +497,68 @@ int cvae_mpc_reference(int n_paths, const double* waypoints, const int32_t* wp_o
                        const double* initial_states, const double* t, int n_t, double* out, double* scalars,
                        void* stream);
 
+/* Validation tables of the model-vs-human comparison (Distribution.py:195-331 velocity JS;
+ * Spatial_Distribution.py:18-161 RMSE_frequency by points, :387-492 by trajectories, :708-931
+ * space-time-velocity surface, :1357-1429 spatiotemporal planes), handle-free.  A population is
+ * ragged: rows float64 [n_rows][stride] on the device, trajectory p owning rows
+ * [offsets[p], offsets[p+1]) (int64 [n_traj+1], on the device AND the same table on the host,
+ * offsets_host, which is validated — monotone, ending at n_rows — before anything is launched).
+ * Model tracks: stride 4 (x, y, theta, v), t_col = -1 (t = i * dt, np.arange(n) * dt :733).
+ * Human tracks: stride 3 (x, y, t), v_col = -1 (velocities in separate per-row arrays).
+ * Edge counts of 0 switch a table off.  Limits: 1024 edges per axis, 65536 grid cells, 4096
+ * surface cells, 4096 time slices, fewer than 2^28 points, |x|, |y|, |v| < 1024. */
+typedef struct cvae_val_config {
+  double dt;                /* model time step (used when t_col < 0) */
+  int stride;               /* doubles per row */
+  int x_col, y_col;         /* columns of x and y */
+  int t_col;                /* column of t, or -1: t = (double)i * dt */
+  int v_col;                /* column of v, or -1: v comes from the v arrays */
+  int coord_col;            /* the surface's coordinate column (axis 'x' or 'y') */
+  int subsample;            /* point counts: n > subsample -> np.linspace(0, n-1, subsample, dtype=int) (:33-50) */
+  int surf_min_rows;        /* the surface skips shorter trajectories (:766) */
+  int n_v_edges;            /* np.linspace(vmin, vmax, 50) (Distribution.py:312) */
+  int n_x_edges, n_y_edges; /* _get_grid_edges (:360-384): the scene has (n_y-1) x (n_x-1) cells */
+  int n_coord_edges, n_time_edges; /* np.linspace(.., 41) (:900-901) */
+  int n_slice_edges;        /* np.arange(t_min, t_max + 1e-9, interval) (:1403); < 2 = no slices */
+  int block_waves;          /* trajectories (waves) per workgroup, 1..8; 0 = default */
+} cvae_val_config;
+
+/* Device tables cvae_val_accumulate ADDS into (zero them first).  Sums are 64-bit fixed point,
+ * quantum 2^-24, each addend rounded to nearest: integer adds, so bit-identical whatever the order. */
+typedef struct cvae_val_tables {
+  uint32_t* hist_v;     /* [n_v_edges-1]                np.histogram (Distribution.py:315-316) */
+  uint32_t* h_points;   /* [n_y-1][n_x-1]               np.histogram2d(..).T (:118-122) */
+  uint32_t* h_traj;     /* [n_y-1][n_x-1]               _count_trajectories_per_grid (:387-430) */
+  uint32_t* surf_cnt;   /* [n_time-1][n_coord-1]        count_surface (:904-914) */
+  int64_t* surf_sum;    /* [n_time-1][n_coord-1]        v_surface before the division (:913) */
+  uint32_t* slice_cnt;  /* [n_slice_edges-1]            points per time slice (:1411-1414) */
+  int64_t* slice_sx;    /* [n_slice_edges-1]            sum of x per slice (:1417-1418) */
+  int64_t* slice_sy;    /* [n_slice_edges-1]            sum of y per slice */
+} cvae_val_tables;
+
+/* Ranges pass (replaces the np.min / np.max of Distribution.py:310-311, Spatial_Distribution.py
+ * :800-832 and :1401-1402): out, 16 x uint64 on the device, receives order-preserving keys of
+ * min, max of v, x, y, t over every point [0..7] and of x, y, t over the trajectories with at
+ * least surf_min_rows rows [8..13] (key: ~bits of a negative value, else bits | 1<<63; an empty population
+ * leaves min > max), the point count [14] and the longest trajectory [15].  v: per-row velocities
+ * when v_col < 0.  Exact and independent of order. */
+int cvae_val_ranges(const cvae_val_config* cfg, int n_traj, const double* rows, int64_t n_rows,
+                    const int64_t* offsets, const int64_t* offsets_host, const double* v, uint64_t* out,
+                    void* stream);
+
+/* Accumulate pass: one launch fills every table whose edge count is set.  edges: the six edge
+ * arrays back to back on the device in the order v, x, y, coordinate, time, slice — built on the
+ * host with numpy as the reference builds them and binary-searched here (np.digitize :415-420,
+ * :906-910; np.histogram's closed last bin :315; np.histogram2d :118), never recomputed.
+ * v_hist / v_surf: per-row velocities for the histogram and the surface when v_col < 0
+ * (calculate_human_velocities Distribution.py:248-296 and _prepare_human_stv_data :765-795 differ).
+ * ranges_host: the 16 words of cvae_val_ranges for this population, on the host (the value and
+ * count bounds of the fixed-point sums are checked from it before the launch). */
+int cvae_val_accumulate(const cvae_val_config* cfg, int n_traj, const double* rows, int64_t n_rows,
+                        const int64_t* offsets, const int64_t* offsets_host, const double* v_hist,
+                        const double* v_surf, const double* edges, const uint64_t* ranges_host,
+                        const cvae_val_tables* tables, void* stream);
+
 const char* cvae_last_error(void);
 int cvae_abi_version(void);
 
