@@ -27,6 +27,7 @@
 #include "cvae_extract.h"
 #include "cvae_mpc.h"
 #include "cvae_metrics.h"
+#include "cvae_safety.h"
 
 namespace {
 
@@ -2232,6 +2233,53 @@ int cvae_val_accumulate(const cvae_val_config* cfg, int n_traj, const double* ro
                             (int)lds));
   hipLaunchKernelGGL(val_accumulate_kernel, dim3(val_grid(n_traj, waves)), dim3(64 * waves), lds,
                      (hipStream_t)stream, c, n_traj, rows, offsets, n_rows, v_hist, v_surf, edges, T);
+  HIPCK(hipGetLastError());
+  return CVAE_OK;
+}
+
+int cvae_safety_metrics(const cvae_safety_config* cfg, const double* log_cols, int64_t n_log_rows,
+                        const int64_t* log_offsets, const int64_t* log_offsets_host, int n_logs,
+                        const int32_t* log_flags, const int32_t* log_flags_host, const double* states,
+                        int64_t n_state_rows, const int64_t* offsets, const int64_t* offsets_host, int n_tracks,
+                        const int32_t* log_of_track, const int32_t* log_of_track_host, double* out_records,
+                        double* out_rows, const int64_t* row_offsets, int64_t n_out_rows, void* stream) {
+  if (!cfg) return fail(CVAE_E_INVALID, "null config");
+  if (cfg->scene < CVAE_SCENE_STATIC || cfg->scene > CVAE_SCENE_UNPREDICTABLE)
+    return fail(CVAE_E_INVALID, "bad scene");
+  if (cfg->block_waves < 0 || cfg->block_waves > SF_MAX_WAVES || cfg->want_rows < 0 || cfg->want_rows > 3 ||
+      (cfg->merge != 0 && cfg->merge != 1))
+    return fail(CVAE_E_INVALID, "bad safety parameter");
+  if (n_logs < 0 || n_tracks < 0 || n_log_rows < 0 || n_state_rows < 0 || n_out_rows < 0)
+    return fail(CVAE_E_INVALID, "bad size");
+  // everything below is checked on the host's copies before anything is launched
+  if (!log_offsets_host || (n_logs && !log_flags_host)) return fail(CVAE_E_INVALID, "null argument");
+  if (log_offsets_host[0] < 0) return fail(CVAE_E_INVALID, "log offsets must start at >= 0");
+  for (int f = 0; f < n_logs; ++f)
+    if (log_offsets_host[f + 1] < log_offsets_host[f]) return fail(CVAE_E_INVALID, "log offsets must be monotone");
+  if (log_offsets_host[n_logs] != n_log_rows) return fail(CVAE_E_INVALID, "log offsets must end at n_log_rows");
+  if (cfg->merge) {
+    int rc = val_offsets(n_tracks, n_state_rows, offsets_host);  // "row offsets must be monotone / end at n_rows"
+    if (rc) return rc;
+  }
+  if (n_tracks && !log_of_track_host) return fail(CVAE_E_INVALID, "null argument");
+  for (int p = 0; p < n_tracks; ++p) {
+    const int lg = log_of_track_host[p];
+    if (lg < 0 || lg >= n_logs) return fail(CVAE_E_INVALID, "log_of_track outside the logs");
+    if (cfg->merge && log_offsets_host[lg + 1] > log_offsets_host[lg] && offsets_host[p + 1] > offsets_host[p] &&
+        !(log_flags_host[lg] & 2))
+      return fail(CVAE_E_INVALID, "a track's log has no finite ego_x/ego_y row");
+  }
+  if (n_tracks == 0) return CVAE_OK;  // nothing that reads is launched
+  if (!out_records || !log_offsets || !log_flags || !log_of_track || (n_log_rows && !log_cols) ||
+      (cfg->merge && (!offsets || (n_state_rows && !states))) || (cfg->want_rows && (!out_rows || !row_offsets)))
+    return fail(CVAE_E_INVALID, "null argument");
+  SfArgs A;
+  A.cols = log_cols; A.log_off = log_offsets; A.log_flags = log_flags; A.states = states; A.off = offsets;
+  A.log_of_track = log_of_track; A.records = out_records; A.rows = cfg->want_rows ? out_rows : nullptr;
+  A.row_off = row_offsets; A.n_log_rows = n_log_rows; A.n_state_rows = n_state_rows; A.n_out_rows = n_out_rows;
+  A.n_logs = n_logs; A.P = n_tracks; A.scene = cfg->scene; A.want_rows = cfg->want_rows; A.merge = cfg->merge;
+  const int waves = cfg->block_waves ? cfg->block_waves : 4;
+  hipLaunchKernelGGL(safety_kernel, dim3(val_grid(n_tracks, waves)), dim3(64 * waves), 0, (hipStream_t)stream, A);
   HIPCK(hipGetLastError());
   return CVAE_OK;
 }

@@ -42,6 +42,10 @@ class CvaeValTables(C.Structure):
                                           "slice_sx", "slice_sy")]
 
 
+class CvaeSafetyConfig(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("scene", "want_rows", "block_waves", "merge")]
+
+
 class CvaeAdamConfig(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
@@ -130,6 +134,11 @@ _SIGS = {
     # cfg, n_traj, rows, n_rows, offsets, offsets_host, v_hist, v_surf, edges, ranges_host, tables, stream
     "cvae_val_accumulate": (_i, [C.POINTER(CvaeValConfig), _i, _v, _i64, _v, _v, _v, _v, _v, _v,
                                  C.POINTER(CvaeValTables), _v]),
+    # cfg, log_cols, n_log_rows, log_offsets, log_offsets_host, n_logs, log_flags, log_flags_host, states,
+    # n_state_rows, offsets, offsets_host, n_tracks, log_of_track, log_of_track_host, out_records, out_rows,
+    # row_offsets, n_out_rows, stream
+    "cvae_safety_metrics": (_i, [C.POINTER(CvaeSafetyConfig), _v, _i64, _v, _v, _i, _v, _v, _v, _i64, _v, _v, _i,
+                                 _v, _v, _v, _v, _v, _i64, _v]),
     "cvae_set_timing": (_i, [_v, _i]),
     "cvae_kernel_times": (_i, [_v, C.c_char_p, _i, C.POINTER(_f), _i]),
     "cvae_last_error": (C.c_char_p, []),

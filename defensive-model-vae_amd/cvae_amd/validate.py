@@ -381,14 +381,11 @@ def metrics(tracks, ref: HumanReference, axis="x", time_interval=5.0):
     return out
 
 
-def validate_checkpoint(model_path, start_states, ref: HumanReference, seq_len=10, dim=3, latent_dim=8, axis="x",
-                        time_interval=5.0, z=None, timings=None):
-    """Generate, track and score a checkpoint without the states leaving the device.
-
-    ``start_states``: [P, 5] (x, y, theta, vx, vy), the start rows ``get_start_conditions_from_csv``
-    reads.  Runs ``generate_trajectories`` from each start position, tracks every generated path
-    as ``Distribution.py:83-105`` does (N=30, control horizon 20, the scene's dt, total time = the
-    last waypoint's), then ``metrics``.  ``timings``: a dict that receives seconds per stage."""
+def _generate_and_track(model_path, start_states, device, dt, seq_len, dim, latent_dim, z, timings):
+    """The stages ``validate_checkpoint`` and ``safety.checkpoint_safety`` share: ``generate_trajectories``
+    from each start position, then every generated path tracked as ``Distribution.py:83-105`` does
+    (N=30, control horizon 20, the scene's dt, total time = the last waypoint's).  Returns the
+    ``DeviceTracks`` and ``lap(name, t0)``, which records a stage's seconds in ``timings``."""
     import time
 
     from . import mpc
@@ -398,19 +395,30 @@ def validate_checkpoint(model_path, start_states, ref: HumanReference, seq_len=1
 
     def lap(name, t0):
         if timings is not None:
-            torch.cuda.synchronize(ref.device)
+            torch.cuda.synchronize(device)
             timings[name] = time.perf_counter() - t0
         return time.perf_counter()
 
     t0 = time.perf_counter()
-    wps = generate_trajectories(model_path, start[:, :2], seq_len, dim, latent_dim, z=z, device=ref.device)
+    wps = generate_trajectories(model_path, start[:, :2], seq_len, dim, latent_dim, z=z, device=device)
     wps = [np.asarray(w, np.float64)[:, [1, 2, 0]].copy() for w in wps]  # [t, x, y] -> [x, y, t] (:77-78)
     for w in wps:
         w[0, 2] = 0.0
     t0 = lap("generate", t0)
-    tracks = mpc.track_batch_device(wps, start, device=ref.device, prediction_horizon=30, control_horizon=20,
-                                    dt=ref.dt)
-    t0 = lap("track", t0)
+    tracks = mpc.track_batch_device(wps, start, device=device, prediction_horizon=30, control_horizon=20, dt=dt)
+    return tracks, lap, lap("track", t0)
+
+
+def validate_checkpoint(model_path, start_states, ref: HumanReference, seq_len=10, dim=3, latent_dim=8, axis="x",
+                        time_interval=5.0, z=None, timings=None):
+    """Generate, track and score a checkpoint without the states leaving the device.
+
+    ``start_states``: [P, 5] (x, y, theta, vx, vy), the start rows ``get_start_conditions_from_csv``
+    reads.  Runs ``generate_trajectories`` from each start position, tracks every generated path
+    as ``Distribution.py:83-105`` does (N=30, control horizon 20, the scene's dt, total time = the
+    last waypoint's), then ``metrics``.  ``timings``: a dict that receives seconds per stage."""
+    tracks, lap, t0 = _generate_and_track(model_path, start_states, ref.device, ref.dt, seq_len, dim, latent_dim, z,
+                                          timings)
     out = metrics(tracks, ref, axis=axis, time_interval=time_interval)
     lap("metrics", t0)
     return out

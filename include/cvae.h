@@ -559,6 +559,53 @@ int cvae_val_accumulate(const cvae_val_config* cfg, int n_traj, const double* ro
                         const double* v_surf, const double* edges, const uint64_t* ranges_host,
                         const cvae_val_tables* tables, void* stream);
 
+/* Safety metrics of tracked trajectories (SUT_Testing/Defensive_Testing.py find_best_start_row
+ * :156-163, compute_ego_kinematics :130-153, merge_trajectory_into_csv :166-205;
+ * SUT_Testing/tools/Metrics_Calculation.py filter_* :143-210, add_ttc_column :264-274,
+ * _pet_two_rays :19-63, add_pet_column :277-286, add_jerk_column :300-328 and the scenario
+ * sub-window statistics of main() :412-456 with metric = "TTC"), handle-free, one launch for a
+ * whole population.  The merged log is never written to memory.
+ *
+ * Logs: log_cols float64 [20][n_log_rows] on the device, column-major, the columns
+ *   frame, sim_time, ego_{x,y,vx,vy,ax,ay,yaw}, sv1_{x,y,vx,vy,ax,yaw}, sv2_{x,y,vx,vy,yaw}
+ * of all logs stacked, log f owning rows [log_offsets[f], log_offsets[f+1]) (int64 [n_logs+1]);
+ * log_flags int32 [n_logs]: bit 0 = the log has a sim_time column (else the scene's default step,
+ * _default_dt_jerk :289-297), bit 1 = it has a row with finite ego_x and ego_y — the caller's
+ * assertion (cvae_amd.safety.pack_logs computes it when it packs the columns): the columns are on
+ * the device and the host check below reads this flag, not the data; a track whose distances are
+ * all NaN all the same gets status NO_START from the kernel.
+ * Tracks: the ragged layout cvae_mpc_track writes — states float64 [n_state_rows][4] (x, y, theta,
+ * v), track p owning rows [offsets[p], offsets[p+1]) (int64 [n_tracks+1]); log_of_track int32
+ * [n_tracks].  Every table comes twice: on the device, and the same on the host (*_host), which is
+ * validated before anything is launched — offsets monotone and ending at their row count,
+ * log_of_track in range, and (merge) no track on a log without a finite ego_x/ego_y row
+ * (np.nanargmin raises there).  n_tracks = 0, an empty track and an empty log are legal (status
+ * EMPTY; nothing that reads is launched for n_tracks = 0).
+ *
+ * merge = 1: the track is written back from the nearest log row on and the log truncated where the
+ * track ends; merge = 0: the logs as recorded (compute_metric_from_csv), states/offsets unused.
+ * out_records: float64 [n_tracks][18] = status (0 OK, 1 NO_WINDOW: no row meets the scenario's
+ * start predicate, the reference raises; 2 EMPTY; 3 NO_START: a non-finite first state), start, L,
+ * i0, i1 (-1: none), window rows, sub-window rows, then count/mean/min of TTC > 0, count/mean/min
+ * of finite PET >= 0, count/mean/max of finite |JERK|, the scenario's "max longitudinal
+ * deceleration" value and max ego_yaw over the TTC-valid rows.
+ * want_rows (bit 0: TTC, PET, JERK of the window rows; bit 1: the seven merged ego columns of every
+ * merged row): out_rows float64 [10][n_out_rows], track p owning rows [row_offsets[p],
+ * row_offsets[p+1]) (int64 [n_tracks+1], device; its log's row count), indexed by merged row; rows
+ * the kernel does not write keep the caller's fill. */
+typedef struct cvae_safety_config {
+  int scene;        /* CVAE_SCENE_* */
+  int want_rows;    /* 0, or bits 0 / 1 as above */
+  int block_waves;  /* tracks (waves) per workgroup, 1..8; 0 = default (4) */
+  int merge;        /* 1: write the tracks back; 0: the logs as recorded */
+} cvae_safety_config;
+int cvae_safety_metrics(const cvae_safety_config* cfg, const double* log_cols, int64_t n_log_rows,
+                        const int64_t* log_offsets, const int64_t* log_offsets_host, int n_logs,
+                        const int32_t* log_flags, const int32_t* log_flags_host, const double* states,
+                        int64_t n_state_rows, const int64_t* offsets, const int64_t* offsets_host, int n_tracks,
+                        const int32_t* log_of_track, const int32_t* log_of_track_host, double* out_records,
+                        double* out_rows, const int64_t* row_offsets, int64_t n_out_rows, void* stream);
+
 const char* cvae_last_error(void);
 int cvae_abi_version(void);
 
